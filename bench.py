@@ -1,7 +1,19 @@
 """Benchmark of the MI355X DPF / dense-PIR hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and no more: set up, warm up, time
+the K steps, write the outputs if asked, print the line.  --full adds every
+other leg described below (`pir` and its handle_request legs, `cpu_baseline`,
+and at N > 1 the library_multi_device child); the --skip-* options trim it.
+
+--dump-outputs DIR writes what the last timed step left in HBM, as float64:
+DIR/c5_leaves.npy (DIR/c5_leaves_rank<r>.npy at N > 1), rows {leaf index
+high 32 bits, low 32 bits, the uint32 element, the IntModN element's high 32
+bits, its low 32 bits} of a fixed, seeded sample of 4096-leaf runs (the
+domain's first and last run and alpha's among them).  The key and the sample
+depend only on the arguments, so two builds compare output for output.
 
 Headline (`value`): full-domain DPF evaluation leaves/s over the whole job —
 config c5 of BASELINE.json: one key, log_domain_size = 32,
@@ -191,6 +203,34 @@ def key_arrays(dpf, key, level, device):
         corr=corr, party=key.party)
 
 
+DUMP_RUN_LEAVES = 4096
+DUMP_RANDOM_RUNS = 256  # + first, last, alpha's: 259 x 4096 rows x 5 float64 = 42 MB
+
+
+def dump_c5_outputs(dirname, out, leaf_lo, leaf_hi, alpha, rank, world):
+    """--dump-outputs: a fixed sample of this rank's leaves [leaf_lo, leaf_hi)
+    as they lie in `out` after the last timed step (16 bytes per leaf, the
+    host layout of the tuple), every 32-bit half exact in float64."""
+    run = min(DUMP_RUN_LEAVES, leaf_hi - leaf_lo)
+    nruns = (leaf_hi - leaf_lo) // run
+    rng = np.random.default_rng(20260 + rank)
+    starts = {leaf_lo, leaf_hi - run}
+    if leaf_lo <= alpha < leaf_hi:
+        starts.add(min(leaf_lo + (alpha - leaf_lo) // run * run, leaf_hi - run))
+    starts |= {leaf_lo + int(i) * run for i in rng.integers(0, nruns, DUMP_RANDOM_RUNS)}
+    lo32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    rows = []
+    for s in sorted(starts):
+        a = (s - leaf_lo) * 16
+        w = out[a:a + run * 16].cpu().numpy().view(np.uint64).reshape(-1, 2)
+        idx = np.arange(s, s + run, dtype=np.uint64)
+        rows.append(np.stack([idx >> s32, idx & lo32, w[:, 1] & lo32, w[:, 0] >> s32,
+                              w[:, 0] & lo32], axis=1).astype(np.float64))
+    os.makedirs(dirname, exist_ok=True)
+    name = "c5_leaves.npy" if world == 1 else "c5_leaves_rank%d.npy" % rank
+    np.save(os.path.join(dirname, name), np.concatenate(rows))
+
+
 def bench_dpf(args, world, rank, device):
     vt = V.Tuple(V.Integer(32), V.IntModN(64, P64))
     log_domain = args.log_domain
@@ -226,6 +266,9 @@ def bench_dpf(args, world, rank, device):
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
     wall = max_over_ranks(wall, world)
     kernel_ms = max_over_ranks(kernel_ms, world)
+    if args.dump_outputs:
+        assert desc.out_stride == 16  # {uint64 IntModN element, uint32 element | pad}
+        dump_c5_outputs(args.dump_outputs, out, lo * cepb, hi * cepb, alpha, rank, world)
     leaves = total * cepb  # the whole domain, over all ranks
     return dict(wall=wall, kernel_ms=kernel_ms, leaves=leaves, L=L, lo=lo, hi=hi)
 
@@ -861,7 +904,7 @@ def main_experiments(args):
                       "all_correct": all(r.get("correct") for r in rows)}), flush=True)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -893,7 +936,25 @@ def main(argv=None):
     ap.add_argument("--skip-library-multi-device", action="store_true",
                     help="at world > 1, do not run the library_multi_device child")
     ap.add_argument("--library-multi-device-timeout", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the dense-PIR legs, the CPU "
+                         "baseline and, at world > 1, the library_multi_device child")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's leaves to "
+                         "DIR/c5_leaves.npy (float64)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and (args.experiments or args.in_process or args.library_multi_device):
+        ap.error("--dump-outputs goes with the headline run, not with --experiments, "
+                 "--in-process or --library-multi-device")
+    if not (args.full or args.experiments or args.in_process):
+        # the plain run: the headline's legs only (the other modes are asked
+        # for by name and keep their own legs)
+        args.skip_pir = args.skip_cpu_baseline = args.skip_library_multi_device = True
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     # torch.cuda.device_count() does not initialise the GPU on this image
     how, what = launch_decision(args, os.environ, torch.cuda.device_count())
     if how == "error":
@@ -1066,7 +1127,8 @@ def main(argv=None):
         dist.destroy_process_group()
         if rank == 0:
             out["library_multi_device"] = (
-                {"skipped": "--skip-library-multi-device"} if args.skip_library_multi_device
+                {"skipped": "--skip-library-multi-device" if args.full else "run without --full"}
+                if args.skip_library_multi_device
                 else run_library_multi_device(library_multi_device_cmd(ranks, args),
                                               args.library_multi_device_timeout))
     if rank == 0:

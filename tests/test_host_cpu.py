@@ -341,6 +341,57 @@ def test_bench_lds_roofline_of_the_many_query_scan():
     assert abs(r["frac"] - r["floor_ms"] / 4.0) < 1e-12
 
 
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs: the rows are {leaf index, uint32 element,
+    IntModN element} in exact 32-bit halves of the 16-byte leaves, the sample
+    holds the slice's first and last run and alpha's, and the same arguments
+    give the same file."""
+    import numpy as np
+    import torch
+    import bench
+    run, lo, hi = bench.DUMP_RUN_LEAVES, 3 << 20, 5 << 20
+    alpha = lo + 77 * run + 5
+    rng = np.random.default_rng(3)
+    words = rng.integers(0, 1 << 63, ((hi - lo), 2), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    out = torch.from_numpy(words.view(np.uint8).reshape(-1))
+    for d in ("a", "b"):
+        bench.dump_c5_outputs(str(tmp_path / d), out, lo, hi, alpha, 0, 1)
+    a = np.load(str(tmp_path / "a" / "c5_leaves.npy"))
+    assert a.dtype == np.float64 and a.shape[1] == 5 and a.nbytes <= 64 << 20
+    assert np.array_equal(a, np.load(str(tmp_path / "b" / "c5_leaves.npy")))
+    assert a.shape[0] % run == 0 and a.shape[0] // run >= 3
+    idx = (a[:, 0].astype(np.uint64) << np.uint64(32)) | a[:, 1].astype(np.uint64)
+    assert np.all(np.diff(idx.astype(np.int64)) > 0)  # sorted, no leaf twice
+    assert idx[0] == lo and idx[-1] == hi - 1 and alpha in idx
+    w = words[(idx - np.uint64(lo)).astype(np.int64)]
+    assert np.array_equal(a[:, 2].astype(np.uint64), w[:, 1] & np.uint64(0xFFFFFFFF))
+    assert np.array_equal((a[:, 3].astype(np.uint64) << np.uint64(32)) | a[:, 4].astype(np.uint64),
+                          w[:, 0])
+    # a rank of a larger job writes its own file
+    bench.dump_c5_outputs(str(tmp_path / "a"), out, lo, hi, alpha, 1, 2)
+    assert np.load(str(tmp_path / "a" / "c5_leaves_rank1.npy")).shape[1] == 5
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full the run times c5 alone; --full brings the other legs
+    back and the --skip-* options trim them; the modes asked for by name
+    keep their legs; --dump-outputs goes with the headline run."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert a.skip_pir and a.skip_cpu_baseline and a.skip_library_multi_device
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.dump_outputs == "d"
+    assert not (a.skip_pir or a.skip_cpu_baseline or a.skip_library_multi_device)
+    a = bench.parse_args(["--full", "--skip-cpu-baseline"])
+    assert a.skip_cpu_baseline and not a.skip_pir
+    for mode in ("--experiments", "--in-process"):
+        a = bench.parse_args([mode])
+        assert not (a.skip_pir or a.skip_cpu_baseline)
+        with pytest.raises(SystemExit):
+            bench.parse_args([mode, "--dump-outputs", "d"])
+
+
 def test_bench_launch_decision():
     """bench.py --gpus N: spawns its N ranks when nothing launched them, runs
     as one rank when WORLD_SIZE matches, refuses a mismatched world size or

@@ -3,10 +3,11 @@
 # (the applied host_write patch) A/B on c3 and the C++ API bench.
 set -o pipefail
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_r06d.log 2>&1 || { echo "bench rc=$?"; tail -20 gpurun_out/bench_r06d.log; exit 1; }
-tail -1 gpurun_out/bench_r06d.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); p=d['pir']; print(d['value'], d['roofline']['frac'], p['ms_per_query'], p['roofline']['frac'], json.dumps(p.get('skip_unselected'))[:600], json.dumps(p.get('handle_request'))[:300], json.dumps(p.get('handle_request_one_eighth'))[:300], d['library'])"
-OUT=gpurun_out/ab_place_r06d.log
+LOGS=${LOGS:-bench_logs}
+mkdir -p $LOGS
+timeout -k 10 400 python -u bench.py --full > $LOGS/bench_r06d.log 2>&1 || { echo "bench rc=$?"; tail -20 $LOGS/bench_r06d.log; exit 1; }
+tail -1 $LOGS/bench_r06d.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); p=d['pir']; print(d['value'], d['roofline']['frac'], p['ms_per_query'], p['roofline']['frac'], json.dumps(p.get('skip_unselected'))[:600], json.dumps(p.get('handle_request'))[:300], json.dumps(p.get('handle_request_one_eighth'))[:300], d['library'])"
+OUT=$LOGS/ab_place_r06d.log
 : > $OUT
 for round in 1 2; do
   for v in new old; do

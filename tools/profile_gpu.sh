@@ -5,7 +5,7 @@
 # Trace pass first, then one PMC pass per counter group (never combined with
 # tracing).  Stops at the first abnormal exit (fault / abort / timeout).
 TAG=${1:-r01}; shift
-ARGS=${@:-"--steps 3 --warmup 1 --skip-cpu-baseline"}
+ARGS=${@:-"--full --steps 3 --warmup 1 --skip-cpu-baseline"}
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
