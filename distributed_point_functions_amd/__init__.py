@@ -5,8 +5,8 @@ Distributed Point Functions library (d346uvcdd/distributed_point_functions)
 behind the reference's API: `DistributedPointFunction`
 (CreateIncremental / GenerateKeys / CreateEvaluationContext / EvaluateNext /
 EvaluateUntil / EvaluateAt / EvaluateAndApply), `DistributedComparisonFunction`
-(GenerateKeys / Evaluate / BatchEvaluate) and `DenseDpfPirServer`
-(HandleRequest).  All evaluation runs in hand-written HIP kernels reached
+(GenerateKeys / Evaluate / BatchEvaluate), `MultipleIntervalContainmentGate`
+(Gen / Eval / BatchEval) and `DenseDpfPirServer` (HandleRequest).  All evaluation runs in hand-written HIP kernels reached
 through the C ABI of include/dpf_amd.h; there is no CPU evaluation path.
 """
 from . import value_types, wire  # noqa: F401
@@ -24,8 +24,10 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".dpf"), name)
     if name in ("DistributedComparisonFunction", "DcfParameters", "DcfKey"):
         return getattr(importlib.import_module(__name__ + ".dcf"), name)
+    if name in ("MultipleIntervalContainmentGate", "MicParameters", "MicKey", "Interval"):
+        return getattr(importlib.import_module(__name__ + ".mic"), name)
     if name in ("DenseDpfPirDatabase", "DenseDpfPirServer", "PirConfig"):
         return getattr(importlib.import_module(__name__ + ".pir"), name)
-    if name in ("kernels", "dpf", "dcf", "pir"):
+    if name in ("kernels", "dpf", "dcf", "mic", "pir"):
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

@@ -116,6 +116,9 @@ def lib():
     _sig(L, "dpf_amd_set_walk_mode", I32, I32)
     _sig(L, "dpf_amd_set_dcf_kernel", I32, I32)
     _sig(L, "dpf_amd_set_prefix_expand", I32, I32)
+    _sig(L, "dpf_amd_set_mic_kernel", I32, I32)
+    _sig(L, "dpf_amd_set_mic_max_grid", I32, I32)
+    _sig(L, "dpf_amd_mic_evaluate", I32, I64, I64, I32, P, P, P, P, P, P, P, P, P, P, P, P, P)
     _bind_tier2(L)
     _lib = L
     return L
@@ -158,6 +161,11 @@ def _bind_tier2(L):
     _sig(L, "dpf_amd_dcf_generate_keys", I32, P, U64, U64, P, SZ, P, BUF,
          ctypes.POINTER(SZ), BUF, ctypes.POINTER(SZ))
     _sig(L, "dpf_amd_dcf_batch_evaluate", I32, P, P, P, I64, P, I64, P, SZ, P)
+    _sig(L, "dpf_amd_mic_create", I32, P, SZ, PP)
+    _sig(L, "dpf_amd_mic_destroy", None, P)
+    _sig(L, "dpf_amd_mic_gen", I32, P, U64, U64, P, I64, P, P, BUF, ctypes.POINTER(SZ), BUF,
+         ctypes.POINTER(SZ))
+    _sig(L, "dpf_amd_mic_batch_eval", I32, P, P, P, I64, P, I64, P)
     _sig(L, "dpf_amd_pir_db_create", I32, PP)
     _sig(L, "dpf_amd_pir_db_insert", I32, P, P, SZ)
     _sig(L, "dpf_amd_pir_db_insert_fixed", I32, P, P, I64, I64)

@@ -22,6 +22,9 @@ LIB = os.path.join(OUT_DIR, "libdpf_amd.so")
 # C++ API consumer test (tests/cpp/api_test.cc) linked against LIB.
 CPP_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "api_test.cc")
 CPP_TEST = os.path.join(OUT_DIR, "cpp_api_test")
+# C++ consumer of the MIC gate (tests/cpp/mic_api_test.cc) linked against LIB.
+MIC_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "mic_api_test.cc")
+MIC_TEST = os.path.join(OUT_DIR, "mic_api_test")
 # C++ API wall-clock bench of the BASELINE configs c1-c3 (tools/cpp_api_bench.cc).
 CPP_BENCH_SRC = os.path.join(ROOT, "tools", "cpp_api_bench.cc")
 CPP_BENCH = os.path.join(OUT_DIR, "cpp_api_bench")
@@ -158,7 +161,7 @@ def build(force: bool = False, jobs: int = 8) -> str:
         subprocess.check_call(["hipcc", "--offload-arch=" + ARCH, "-shared", "-fPIC",
                                "-o", tmp] + objs + ["-lpthread"])
         os.replace(tmp, LIB)
-    for src, exe in ((CPP_TEST_SRC, CPP_TEST), (CPP_BENCH_SRC, CPP_BENCH),
+    for src, exe in ((CPP_TEST_SRC, CPP_TEST), (MIC_TEST_SRC, MIC_TEST), (CPP_BENCH_SRC, CPP_BENCH),
                      (EXP_BENCH_SRC, EXP_BENCH)):
         if os.path.exists(src) and (
                 force or not os.path.exists(exe) or

@@ -14,6 +14,7 @@
 #include "dpf_amd/cuckoo_hashing_sparse_dpf_pir_server.h"
 #include "dpf_amd/dense_dpf_pir_server.h"
 #include "dpf_amd/distributed_comparison_function.h"
+#include "dpf_amd/multiple_interval_containment.h"
 #include "host_device.h"
 #include "dpf_amd/distributed_point_function.h"
 #include "internal.h"
@@ -28,6 +29,9 @@ struct dpf_amd_ctx {
 };
 struct dpf_amd_dcf {
   std::unique_ptr<DistributedComparisonFunction> dcf;
+};
+struct dpf_amd_mic {
+  std::unique_ptr<fss_gates::MultipleIntervalContainmentGate> gate;
 };
 struct dpf_amd_pir_db {
   std::unique_ptr<DenseDpfPirDatabase::Builder> builder =
@@ -406,6 +410,70 @@ int dpf_amd_dcf_batch_evaluate(const dpf_amd_dcf* dcf, const uint8_t* const* key
                                   Span<const uint128>(p.data(), p.size()),
                                   dpf.value_type_descriptor(dpf.num_hierarchy_levels() - 1), out);
   return st.ok() ? DPF_AMD_OK : Fail(st);
+}
+
+// --- MultipleIntervalContainmentGate (dcf/fss_gates/multiple_interval_containment.h) ---
+
+int dpf_amd_mic_create(const uint8_t* parameters, size_t len, dpf_amd_mic** out) {
+  fss_gates::MicParameters p;
+  if (!p.ParseFromArray(parameters, len))
+    return Fail(DPF_AMD_INVALID_ARGUMENT, "malformed MicParameters proto");
+  StatusOr<std::unique_ptr<fss_gates::MultipleIntervalContainmentGate>> g =
+      fss_gates::MultipleIntervalContainmentGate::Create(p);
+  if (!g.ok()) return Fail(g.status());
+  *out = new dpf_amd_mic{std::move(*g)};
+  return DPF_AMD_OK;
+}
+
+void dpf_amd_mic_destroy(dpf_amd_mic* mic) { delete mic; }
+
+int dpf_amd_mic_gen(dpf_amd_mic* mic, uint64_t r_in_lo, uint64_t r_in_hi, const uint64_t* r_out,
+                    int64_t num_r_out, const uint64_t* seeds, const uint64_t* mask_shares,
+                    uint8_t** key0, size_t* key0_len, uint8_t** key1, size_t* key1_len) {
+  if (!mic || num_r_out < 0 || (num_r_out > 0 && !r_out))
+    return Fail(DPF_AMD_INVALID_ARGUMENT, "bad arguments");
+  if ((seeds == nullptr) != (mask_shares == nullptr) && mic->gate->num_intervals() > 0)
+    return Fail(DPF_AMD_INVALID_ARGUMENT, "seeds and mask_shares must be given together");
+  const uint128 r_in = MakeUint128(r_in_hi, r_in_lo);
+  std::vector<uint128> masks = ToU128(r_out, num_r_out);
+  StatusOr<std::pair<fss_gates::MicKey, fss_gates::MicKey>> keys = InternalError("unset");
+  if (seeds) {
+    std::vector<uint128> z0 = ToU128(mask_shares, mic->gate->num_intervals());
+    keys = mic->gate->GenWithSeeds(r_in, std::move(masks), MakeUint128(seeds[1], seeds[0]),
+                                   MakeUint128(seeds[3], seeds[2]),
+                                   Span<const uint128>(z0.data(), z0.size()));
+  } else {
+    keys = mic->gate->Gen(r_in, std::move(masks));
+  }
+  if (!keys.ok()) return Fail(keys.status());
+  int rc = ToBuffer(keys->first.SerializeAsString(), key0, key0_len);
+  if (rc != DPF_AMD_OK) return rc;
+  rc = ToBuffer(keys->second.SerializeAsString(), key1, key1_len);
+  if (rc != DPF_AMD_OK) free(*key0);
+  return rc;
+}
+
+int dpf_amd_mic_batch_eval(dpf_amd_mic* mic, const uint8_t* const* keys,
+                           const size_t* key_lengths, int64_t num_keys, const uint64_t* points,
+                           int64_t num_points, uint64_t* out) {
+  if (!mic || num_keys < 0 || num_points < 0) return Fail(DPF_AMD_INVALID_ARGUMENT, "bad arguments");
+  std::vector<fss_gates::MicKey> ks(num_keys);
+  std::vector<const fss_gates::MicKey*> ptrs(num_keys);
+  for (int64_t i = 0; i < num_keys; ++i) {
+    if (!ks[i].ParseFromArray(keys[i], key_lengths[i]))
+      return Fail(DPF_AMD_INVALID_ARGUMENT, "malformed MicKey proto");
+    ptrs[i] = &ks[i];
+  }
+  std::vector<uint128> p = ToU128(points, num_points);
+  // `out` need not be 16-byte aligned; uint128 in memory is the ABI's {lo, hi}
+  // word pair (little-endian host)
+  std::vector<uint128> res(static_cast<size_t>(num_keys) * mic->gate->num_intervals());
+  Status st = mic->gate->BatchEvalRaw(
+      Span<const fss_gates::MicKey* const>(ptrs.data(), ptrs.size()),
+      Span<const uint128>(p.data(), p.size()), res.data());
+  if (!st.ok()) return Fail(st);
+  if (!res.empty()) memcpy(out, res.data(), res.size() * sizeof(uint128));
+  return DPF_AMD_OK;
 }
 
 int dpf_amd_pir_db_create(dpf_amd_pir_db** out) {

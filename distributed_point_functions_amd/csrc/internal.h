@@ -25,6 +25,9 @@ bool PrefixExpandOff();
 // keeps the prefix de-duplication, the lookup of the stored partial
 // evaluations and the context on the host (the device path's A/B).
 bool HostIncremental();
+// dpf_amd_set_mic_kernel: 0 = the fused MIC kernel, 1 = the reference's two
+// DCF BatchEvaluate calls over replicated keys, combined on the host.
+int MicKernelMode();
 
 // Device-side copy of dpf_amd_value_type plus everything the per-leaf
 // correction needs (kernel argument, < 2 KiB).

@@ -120,6 +120,29 @@ struct DcfArgs {
   int32_t tree_of[kDcfMaxLevels];  // hierarchy level -> tree level
 };
 
+// KMicEvaluate (dcf/fss_gates/multiple_interval_containment.cc:211-308):
+// item (key i, interval j) of n x m; the DCF of the gate has uint128 values,
+// so hierarchy level h is tree level h (log_group_size - 1 correction words
+// per key, one value correction per level).
+struct MicArgs {
+  int64_t n;  // keys
+  int64_t m;  // intervals
+  const uint4* seeds;  // [key]
+  const uint8_t* cb;
+  const int8_t* party;
+  const uint4* x;        // [key] masked inputs
+  const uint4* cw_seed;  // [tree level][key]
+  const uint8_t* ccl;
+  const uint8_t* ccr;
+  const uint4* corrections;  // [hierarchy level][key]
+  const uint4* z;            // [key][interval] output mask shares
+  const uint4* p;            // [interval] lower bounds
+  const uint4* q_prime;      // [interval] (upper bound + 1) mod N
+  uint4* out;                // [key][interval]
+  int32_t log_group_size;
+  int32_t pad;
+};
+
 // KEvaluatePoints: 2 blocks per CU (one 64 KiB table each), 4 waves/SIMD,
 // two points per thread walked in lockstep.
 #ifndef DPF_POINTS_BLOCK
@@ -215,6 +238,10 @@ bool DcfDirectEnabled();
 int LaunchDcfEvaluate(int bn, hipStream_t st, const DcfArgs& a, const VtDev& vt);
 int LaunchAesMmo(int grid, hipStream_t st, const uint4* in, uint4* out, int64_t n,
                  const KeyPair& kp);
+// k_mic.hip; the calling thread's grid cap (dpf_amd_set_mic_max_grid, 0 =
+// the built-in DPF_MIC_MAX_GRID).
+int MicMaxGrid();
+int LaunchMicEvaluate(hipStream_t st, const MicArgs& a);
 // k_pir.hip
 int LaunchGatherRows(int grid, hipStream_t st, int64_t n, const int64_t* src_offset,
                      int64_t opp, int64_t stride, const char* in, char* out,

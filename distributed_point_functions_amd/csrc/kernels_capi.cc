@@ -39,6 +39,8 @@ const int kExpandRootsDefault = [] {
 }();
 thread_local int t_expand_roots = kExpandRootsDefault;
 thread_local int t_dcf_generic = 0;   // dpf_amd_set_dcf_kernel
+thread_local int t_mic_mode = 0;      // dpf_amd_set_mic_kernel
+thread_local int t_mic_max_grid = 0;  // dpf_amd_set_mic_max_grid (0: built-in cap)
 // dpf_amd_set_scan_m4; the process default comes from DPF_AMD_SCAN_M4 (A/B runs)
 const int kScanM4Default = [] {
   const char* e = std::getenv("DPF_AMD_SCAN_M4");
@@ -159,6 +161,8 @@ int LaunchExpandForType(int D, int grid, hipStream_t st, const ExpandArgs& a,
 
 int WalkMode() { return t_walk_mode; }
 bool DcfDirectEnabled() { return t_dcf_generic == 0; }
+int MicKernelMode() { return t_mic_mode; }
+int MicMaxGrid() { return t_mic_max_grid; }
 
 int MakeVtDev(const dpf_amd_value_type& vt, const uint64_t* correction, int party,
               int cepb, VtDev* out) {
@@ -489,6 +493,20 @@ int dpf_amd_set_dcf_kernel(int mode) {
   if (mode < 0 || mode > 1) return -2;
   const int old = t_dcf_generic;
   t_dcf_generic = mode;
+  return old;
+}
+
+int dpf_amd_set_mic_kernel(int mode) {
+  if (mode < 0 || mode > 1) return -2;
+  const int old = t_mic_mode;
+  t_mic_mode = mode;
+  return old;
+}
+
+int dpf_amd_set_mic_max_grid(int blocks) {
+  if (blocks < 0 || blocks > 65536) return -2;
+  const int old = t_mic_max_grid;
+  t_mic_max_grid = blocks;
   return old;
 }
 
@@ -829,6 +847,42 @@ int dpf_amd_dcf_evaluate(int64_t num_keys, const void* seeds, const uint8_t* con
   a.log_domain = log_domain_size;
   for (int h = 0; h < kDcfMaxLevels; ++h) a.tree_of[h] = h < log_domain_size ? tree_level_of[h] : 0;
   return LaunchDcfEvaluate(BnTemplate(dev.bn), (hipStream_t)stream, a, dev);
+}
+
+int dpf_amd_mic_evaluate(int64_t num_keys, int64_t num_intervals, int log_group_size,
+                         const void* seeds, const uint8_t* control_bits, const int8_t* party,
+                         const void* masked_inputs, const void* correction_seeds,
+                         const uint8_t* ccl, const uint8_t* ccr, const void* value_corrections,
+                         const void* mask_shares, const void* lower_bounds,
+                         const void* upper_bounds_plus_one, void* out, void* stream) {
+  if (num_keys < 0 || num_intervals < 0) return SetError(DPF_AMD_INVALID_ARGUMENT, "bad arguments");
+  if (log_group_size < 1 || log_group_size > 127)
+    return SetError(DPF_AMD_INVALID_ARGUMENT, "log_group_size must be in [1, 127]");
+  if (num_keys == 0 || num_intervals == 0) return DPF_AMD_OK;
+  if (num_intervals > (INT64_MAX >> 4) / num_keys)
+    return SetError(DPF_AMD_INVALID_ARGUMENT, "num_keys * num_intervals is too large");
+  if (!seeds || !control_bits || !party || !masked_inputs || !value_corrections ||
+      !mask_shares || !lower_bounds || !upper_bounds_plus_one || !out ||
+      (log_group_size > 1 && (!correction_seeds || !ccl || !ccr)))
+    return SetError(DPF_AMD_INVALID_ARGUMENT, "null device pointer");
+  MicArgs a;
+  a.n = num_keys;
+  a.m = num_intervals;
+  a.seeds = (const uint4*)seeds;
+  a.cb = control_bits;
+  a.party = party;
+  a.x = (const uint4*)masked_inputs;
+  a.cw_seed = (const uint4*)correction_seeds;
+  a.ccl = ccl;
+  a.ccr = ccr;
+  a.corrections = (const uint4*)value_corrections;
+  a.z = (const uint4*)mask_shares;
+  a.p = (const uint4*)lower_bounds;
+  a.q_prime = (const uint4*)upper_bounds_plus_one;
+  a.out = (uint4*)out;
+  a.log_group_size = log_group_size;
+  a.pad = 0;
+  return LaunchMicEvaluate((hipStream_t)stream, a);
 }
 
 int dpf_amd_gather_rows(int64_t num_prefixes, const int64_t* src_offset,

@@ -649,6 +649,86 @@ bool DcfKey::ParseFromArray(const void* data, size_t size) {
   return r.ok();
 }
 
+// --- Interval / MicParameters / MicKey
+// (dcf/fss_gates/multiple_interval_containment.proto) ---
+namespace fss_gates {
+namespace {
+std::string Ser(const Interval& i) {
+  Writer w;
+  if (i.has_lower_bound()) w.Message(1, distributed_point_functions::Ser(i.lower_bound()));
+  if (i.has_upper_bound()) w.Message(2, distributed_point_functions::Ser(i.upper_bound()));
+  return w.Take();
+}
+bool Par(const uint8_t* p, size_t n, Interval* i) {
+  Reader r(p, n);
+  DPF_FOR_EACH_FIELD(r, f, wt) {
+    const uint8_t* d;
+    size_t l;
+    if ((f == 1 || f == 2) && wt == 2) {
+      if (!r.Bytes(&d, &l)) return false;
+      if (!distributed_point_functions::Par(
+              d, l, f == 1 ? i->mutable_lower_bound() : i->mutable_upper_bound()))
+        return false;
+    } else if (!r.Skip(wt)) {
+      return false;
+    }
+  }
+  return r.ok();
+}
+}  // namespace
+
+std::string MicParameters::SerializeAsString() const {
+  Writer w;
+  w.I32(1, log_group_size());
+  for (const Interval& i : intervals()) w.Message(2, Ser(i));
+  return w.Take();
+}
+bool MicParameters::ParseFromArray(const void* data, size_t size) {
+  *this = MicParameters();
+  Reader r(data, size);
+  DPF_FOR_EACH_FIELD(r, f, wt) {
+    const uint8_t* d;
+    size_t l;
+    uint64_t v;
+    if (f == 1 && wt == 0) {
+      if (!r.Varint(&v)) return false;
+      set_log_group_size(static_cast<int32_t>(v));
+    } else if (f == 2 && wt == 2) {
+      if (!r.Bytes(&d, &l) || !Par(d, l, add_intervals())) return false;
+    } else if (!r.Skip(wt)) {
+      return false;
+    }
+  }
+  return r.ok();
+}
+
+std::string MicKey::SerializeAsString() const {
+  Writer w;
+  if (has_dcfkey()) w.Message(1, dcfkey().SerializeAsString());
+  for (const Value::Integer& z : output_mask_share())
+    w.Message(2, distributed_point_functions::Ser(z));
+  return w.Take();
+}
+bool MicKey::ParseFromArray(const void* data, size_t size) {
+  *this = MicKey();
+  Reader r(data, size);
+  DPF_FOR_EACH_FIELD(r, f, wt) {
+    const uint8_t* d;
+    size_t l;
+    if (f == 1 && wt == 2) {
+      if (!r.Bytes(&d, &l) || !mutable_dcfkey()->ParseFromArray(d, l)) return false;
+    } else if (f == 2 && wt == 2) {
+      if (!r.Bytes(&d, &l) ||
+          !distributed_point_functions::Par(d, l, add_output_mask_share()))
+        return false;
+    } else if (!r.Skip(wt)) {
+      return false;
+    }
+  }
+  return r.ok();
+}
+}  // namespace fss_gates
+
 // --- pir/hashing/hash_family_config.proto, CuckooHashingParams ---
 std::string HashFamilyConfig::SerializeAsString() const {
   Writer w;

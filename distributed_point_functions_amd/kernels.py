@@ -235,6 +235,59 @@ class forced_dcf_kernel:
         _lib.lib().dpf_amd_set_dcf_kernel(self.prev)
 
 
+class forced_mic_kernel:
+    """Context manager selecting this thread's MIC gate BatchEval strategy
+    (dpf_amd_set_mic_kernel: 0 fused kernel, 1 the reference's two DCF batch
+    evaluations combined on the host)."""
+
+    def __init__(self, mode: int):
+        self.mode = mode
+
+    def __enter__(self):
+        prev = _lib.lib().dpf_amd_set_mic_kernel(self.mode)
+        if prev < 0:
+            raise ValueError("mic kernel mode must be 0 or 1")
+        self.prev = prev
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().dpf_amd_set_mic_kernel(self.prev)
+
+
+class forced_mic_max_grid:
+    """Context manager capping the blocks of this thread's fused MIC launches
+    (dpf_amd_set_mic_max_grid; 0 = the built-in cap)."""
+
+    def __init__(self, blocks: int):
+        self.blocks = blocks
+
+    def __enter__(self):
+        prev = _lib.lib().dpf_amd_set_mic_max_grid(self.blocks)
+        if prev < 0:
+            raise ValueError("mic grid cap must be in [0, 65536]")
+        self.prev = prev
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().dpf_amd_set_mic_max_grid(self.prev)
+
+
+def mic_evaluate(log_group_size, seeds, control_bits, party, masked_inputs, cw_seeds, ccl, ccr,
+                 value_corrections, mask_shares, lower_bounds, upper_bounds_plus_one, out=None):
+    """Fused MIC gate evaluation (dpf_amd_mic_evaluate): per-key seeds (n, 2),
+    control bits / party (n,), masked inputs (n, 2); correction words
+    [(log_group_size - 1) * n]; value corrections [log_group_size * n];
+    mask shares (n * m, 2); bounds (m, 2).  Returns (n * m, 2) int64."""
+    n, m = seeds.shape[0], lower_bounds.shape[0]
+    if out is None:
+        out = torch.empty((n * m, 2), dtype=torch.int64, device=seeds.device)
+    check(_lib.lib().dpf_amd_mic_evaluate(
+        n, m, log_group_size, dptr(seeds), dptr(control_bits), dptr(party), dptr(masked_inputs),
+        dptr(cw_seeds), dptr(ccl), dptr(ccr), dptr(value_corrections), dptr(mask_shares),
+        dptr(lower_bounds), dptr(upper_bounds_plus_one), dptr(out), stream_ptr()))
+    return out
+
+
 def evaluate_points(seeds, control_bits, paths, paths_rightshift, num_levels,
                     cw_seeds, ccl, ccr, desc, block_index=None, party=None,
                     party_all: int = 0, value_corrections=None,

@@ -233,6 +233,20 @@ int dpf_amd_set_prefix_expand(int mode);
  * setting, or -2 for an invalid mode (unchanged). */
 int dpf_amd_set_dcf_kernel(int mode);
 
+/* Test hook: the calling thread's MultipleIntervalContainmentGate BatchEval
+ * strategy.  0 = the fused kernel (dpf_amd_mic_evaluate: every key uploaded
+ * once, one launch), 1 = the reference's composition (two DCF BatchEvaluate
+ * calls over num_keys * num_intervals replicated key pointers, combined on
+ * the host).  Returns the previous setting, or -2 for an invalid mode
+ * (unchanged). */
+int dpf_amd_set_mic_kernel(int mode);
+
+/* Test hook: the most blocks a dpf_amd_mic_evaluate launch of the calling
+ * thread uses (lanes loop over the items beyond it); 0 = the built-in cap.
+ * Returns the previous setting, or -2 for a value outside [0, 65536]
+ * (unchanged). */
+int dpf_amd_set_mic_max_grid(int blocks);
+
 /* Fused single-path evaluation: EvaluateSeeds from the given seeds along
  * `paths` (one AES per level, per-lane key select) + HashExpandedSeeds +
  * correction of element block_index[i] (EvaluateAtImpl h:1013-1063 and the
@@ -290,6 +304,32 @@ int dpf_amd_dcf_evaluate(int64_t num_keys, const void* seeds,
                          const uint8_t* correction_controls_right,
                          const dpf_amd_value_type* vt,
                          const void* value_corrections, void* out,
+                         void* stream);
+
+/* Fused fss_gates::MultipleIntervalContainmentGate::BatchEval
+ * (dcf/fss_gates/multiple_interval_containment.cc:211-308, Fig. 14 Eval of
+ * eprint 2020/1392) over the gate's DCF (log domain log_group_size in
+ * [1, 127], uint128 values: hierarchy level h is tree level h).  Item (key i,
+ * interval j) walks x_p = x[i] - 1 - lower_bounds[j] and x_q' = x[i] - 1 -
+ * upper_bounds_plus_one[j] (mod N = 2^log_group_size) down key i's tree in
+ * lockstep, sums both DCF outputs and writes
+ *   out[i * num_intervals + j] = ((party[i] ? (x[i] > p_j) - (x[i] > q'_j) : 0)
+ *                                 - s_p + s_q' + mask_shares[i][j]) mod N.
+ * Device arrays of 128-bit {lo, hi} words unless noted: seeds, control_bits
+ * (uint8), party (int8) and masked_inputs per key; correction words
+ * [tree level][key] (log_group_size - 1 levels; may be NULL at
+ * log_group_size 1); value_corrections [level][key]; mask_shares
+ * [key][interval]; the bounds per interval. */
+int dpf_amd_mic_evaluate(int64_t num_keys, int64_t num_intervals,
+                         int log_group_size, const void* seeds,
+                         const uint8_t* control_bits, const int8_t* party,
+                         const void* masked_inputs,
+                         const void* correction_seeds,
+                         const uint8_t* correction_controls_left,
+                         const uint8_t* correction_controls_right,
+                         const void* value_corrections,
+                         const void* mask_shares, const void* lower_bounds,
+                         const void* upper_bounds_plus_one, void* out,
                          void* stream);
 
 /* Gathers the per-prefix output slices of an incremental evaluation
@@ -483,6 +523,27 @@ int dpf_amd_dcf_batch_evaluate(const dpf_amd_dcf* dcf,
                                const uint64_t* points, int64_t num_points,
                                const uint8_t* value_type,
                                size_t value_type_len, void* out);
+
+/* fss_gates::MultipleIntervalContainmentGate (dcf/fss_gates/
+ * multiple_interval_containment.h:41-104).  Parameters and keys cross as
+ * MicParameters / MicKey protos; 128-bit values as {lo, hi} word pairs.
+ * Gen: `r_out` holds num_intervals output masks; `seeds` (4 words: DCF root
+ * seed0 lo, hi, seed1 lo, hi) and `mask_shares` (num_intervals party-0 shares
+ * z_0) replace the CSPRNG for fixtures — both NULL = CSPRNG, both non-NULL =
+ * seeded.  BatchEval evaluates keys[i] at points[i] and writes num_keys *
+ * num_intervals values, key i's interval j at i * num_intervals + j. */
+typedef struct dpf_amd_mic dpf_amd_mic;
+int dpf_amd_mic_create(const uint8_t* parameters, size_t len, dpf_amd_mic** out);
+void dpf_amd_mic_destroy(dpf_amd_mic* mic);
+int dpf_amd_mic_gen(dpf_amd_mic* mic, uint64_t r_in_lo, uint64_t r_in_hi,
+                    const uint64_t* r_out, int64_t num_r_out,
+                    const uint64_t* seeds, const uint64_t* mask_shares,
+                    uint8_t** key0, size_t* key0_len, uint8_t** key1,
+                    size_t* key1_len);
+int dpf_amd_mic_batch_eval(dpf_amd_mic* mic, const uint8_t* const* keys,
+                           const size_t* key_lengths, int64_t num_keys,
+                           const uint64_t* points, int64_t num_points,
+                           uint64_t* out);
 
 /* Dense PIR database: DenseDpfPirDatabase::Builder (pir/dense_dpf_pir_database.h
  * :41-62) with the records resident in HBM. */

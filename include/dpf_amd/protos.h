@@ -4,6 +4,7 @@
 // messages are byte-compatible with the reference.
 //   dpf/distributed_point_function.proto:25-171
 //   pir/private_information_retrieval.proto:28-151
+//   dcf/fss_gates/multiple_interval_containment.proto:25-60
 #ifndef DPF_AMD_PROTOS_H_
 #define DPF_AMD_PROTOS_H_
 
@@ -332,6 +333,49 @@ class DcfKey {
   bool has_key_ = false;
   DpfKey key_;
 };
+
+// --- MIC gate messages (dcf/fss_gates/multiple_interval_containment.proto) --
+
+namespace fss_gates {
+
+class Interval {
+ public:
+  DPF_AMD_MESSAGE_FIELD(Value::Integer, lower_bound)
+  DPF_AMD_MESSAGE_FIELD(Value::Integer, upper_bound)
+
+ private:
+  bool has_lower_bound_ = false, has_upper_bound_ = false;
+  Value::Integer lower_bound_, upper_bound_;
+};
+
+class MicParameters {
+ public:
+  DPF_AMD_SCALAR_FIELD(int32_t, log_group_size)
+  DPF_AMD_REPEATED_FIELD(Interval, intervals)
+  std::string SerializeAsString() const;
+  bool ParseFromString(const std::string& data) { return ParseFromArray(data.data(), data.size()); }
+  bool ParseFromArray(const void* data, size_t size);
+
+ private:
+  int32_t log_group_size_ = 0;
+  std::vector<Interval> intervals_;
+};
+
+class MicKey {
+ public:
+  DPF_AMD_MESSAGE_FIELD(DcfKey, dcfkey)
+  DPF_AMD_REPEATED_FIELD(Value::Integer, output_mask_share)
+  std::string SerializeAsString() const;
+  bool ParseFromString(const std::string& data) { return ParseFromArray(data.data(), data.size()); }
+  bool ParseFromArray(const void* data, size_t size);
+
+ private:
+  bool has_dcfkey_ = false;
+  DcfKey dcfkey_;
+  std::vector<Value::Integer> output_mask_share_;
+};
+
+}  // namespace fss_gates
 
 // --- PIR messages (pir/private_information_retrieval.proto) ---------------
 

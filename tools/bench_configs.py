@@ -17,6 +17,11 @@ pirgrid the reference's PIR benchmark grid (dense_dpf_pir_database_benchmark.cc:
 dcf DistributedComparisonFunction BatchEvaluate, log_domain 32, uint64
     (distributed_comparison_function_benchmark.cc:31-63 shape): 1024 keys
     via the Tier-2 API, and 2^20 (key, point) pairs through the fused kernel
+mic MultipleIntervalContainmentGate BatchEval, log_group_size 64, 10 intervals
+    (multiple_interval_containment_benchmark.cc shape): 1000 and 2^16 keys,
+    the fused kernel against the reference's composition (two DCF batch
+    evaluations over keys x intervals replicated keys, host combine), each
+    end to end through the Tier-2 API and event-timed at the Tier-1 seam
 cuckoo  cuckoo-hashed sparse PIR: 2^20 keyword records
     (16-byte keys, 240-byte values), 1.5 x 2^20 buckets, 3 SHA-256 hash
     functions; two plain servers, one keyword query (3 DPF keys per server)
@@ -491,6 +496,144 @@ def dcf(dev, reps):
             "lds_frac": aes * 160 / t_k / LDS_PEAK_LOOKUPS, "correct": bool(ok)}
 
 
+def _mic_shape(dev, reps, nkeys, m, n_log, distinct):
+    """One MIC shape: `nkeys` keys (`distinct` generated, repeated) x `m`
+    intervals.  End to end through the C ABI and event-timed at the Tier-1
+    seam, the fused kernel against the reference's composition (two DCF batch
+    evaluations over nkeys * m replicated keys), alternating."""
+    from distributed_point_functions_amd.mic import (Interval, MicParameters,
+                                                     MultipleIntervalContainmentGate)
+    from distributed_point_functions_amd._lib import check, dptr, stream_ptr
+    rng = random.Random(14 + nkeys)
+    N = 1 << n_log
+    intervals = [tuple(sorted((rng.randrange(N), rng.randrange(N)))) for _ in range(m)]
+    g = MultipleIntervalContainmentGate.create(
+        MicParameters(n_log, [Interval(p, q) for p, q in intervals]))
+    r_out = [rng.randrange(N) for _ in range(m)]
+    r_in = [rng.randrange(N) for _ in range(distinct)]
+    pairs = [g.gen(r, r_out, seeds=(2 * i + 7, 2 * i + 8),
+                   mask_shares=[rng.getrandbits(128) for _ in range(m)])
+             for i, r in enumerate(r_in)]
+    rep = nkeys // distinct
+    sel = [i // rep for i in range(nkeys)]  # entry -> generated key (np.repeat's order)
+    k0, k1 = [pairs[i][0] for i in sel], [pairs[i][1] for i in sel]
+    xs = [rng.randrange(N) for _ in range(nkeys)]
+    masked = [(x + r_in[i]) % N for x, i in zip(xs, sel)]
+
+    # Tier 2, wall clock: each trial times one mode after the other
+    api = {0: [], 1: []}
+    api_reps = {0: max(1, reps // 2), 1: max(1, reps // 4)}
+    for _ in range(3):
+        for mode in (0, 1):
+            with kernels.forced_mic_kernel(mode):
+                api[mode].append(wall_time(lambda: g.batch_eval(k0, masked), api_reps[mode]))
+    with kernels.forced_mic_kernel(0):
+        f0, f1 = g.batch_eval(k0, masked), g.batch_eval(k1, masked)
+    with kernels.forced_mic_kernel(1):
+        c0 = g.batch_eval(k0, masked)
+    ok = f0 == c0 and all(
+        (f0[i * m + j] + f1[i * m + j] - r_out[j]) % N == int(p <= xs[i] <= q)
+        for i in range(0, nkeys, max(1, nkeys // 512)) for j, (p, q) in enumerate(intervals))
+
+    # Tier 1: device arrays of party 0's keys
+    H, L = n_log, n_log - 1
+    u = lambda v: (v & M64, v >> 64)  # noqa: E731
+    seeds = np.zeros((distinct, 2), np.uint64)
+    cw = np.zeros((L, distinct, 2), np.uint64)
+    ccl = np.zeros((L, distinct), np.uint8)
+    ccr = np.zeros((L, distinct), np.uint8)
+    corr = np.zeros((H, distinct, 2), np.uint64)
+    z = np.zeros((distinct, m, 2), np.uint64)
+    for i, (k, _) in enumerate(pairs):
+        dk = k.dcfkey.key
+        seeds[i] = u(dk.seed)
+        for a in range(L):
+            c = dk.correction_words[a]
+            cw[a, i] = u(c.seed)
+            ccl[a, i], ccr[a, i] = int(c.control_left), int(c.control_right)
+        for h in range(H):
+            vals = (dk.last_level_value_correction if h == H - 1
+                    else dk.correction_words[h].value_correction)
+            corr[h, i] = u(decode_value(V.Integer(128), vals[0])[0])
+        z[i] = [u(s) for s in k.output_mask_share]
+    tile = lambda a, axis, r: np.ascontiguousarray(np.repeat(a, r, axis=axis))  # noqa: E731
+    T = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)  # noqa
+    x_np = np.array([u(x) for x in masked], np.uint64)
+    d_p = kernels.u128_tensor([p for p, _ in intervals], dev)
+    d_q = kernels.u128_tensor([(q + 1) % N for _, q in intervals], dev)
+    fused_in = [T(tile(seeds, 0, rep)), torch.zeros(nkeys, dtype=torch.uint8, device=dev),
+                torch.zeros(nkeys, dtype=torch.int8, device=dev), T(x_np), T(tile(cw, 1, rep)),
+                T(tile(ccl, 1, rep)), T(tile(ccr, 1, rep)), T(tile(corr, 1, rep)),
+                T(tile(z, 0, rep).reshape(-1, 2)), d_p, d_q]
+    out_f = torch.empty((nkeys * m, 2), dtype=torch.int64, device=dev)
+
+    def fused():
+        kernels.mic_evaluate(H, *fused_in, out=out_f)
+
+    # the composition's launches: the DCF kernel over nkeys * m replicated keys, twice
+    items = nkeys * m
+    pts = [[(x + N - 1 - b) % N for x in masked for b in bs]
+           for bs in ([p for p, _ in intervals], [(q + 1) % N for _, q in intervals])]
+    d_pts = [T(np.array([u(v) for v in p], np.uint64)) for p in pts]
+    c_seeds, c_cw = T(tile(seeds, 0, rep * m)), T(tile(cw, 1, rep * m))
+    c_ccl, c_ccr = T(tile(ccl, 1, rep * m)), T(tile(ccr, 1, rep * m))
+    c_corr = T(tile(corr, 1, rep * m))
+    c_cb = torch.zeros(items, dtype=torch.uint8, device=dev)
+    c_party = torch.zeros(items, dtype=torch.int8, device=dev)
+    outs = [torch.empty((items, 2), dtype=torch.int64, device=dev) for _ in range(2)]
+    mirror = DistributedPointFunction.create_incremental(
+        [DpfParameters(h, V.Integer(128)) for h in range(H)])
+    desc = mirror.value_type_descriptor(H - 1)
+    tree_of = np.arange(H, dtype=np.int32)
+    tree_c = tree_of.ctypes.data_as(ctypes.c_void_p)
+
+    def composed():
+        for d_x, o in zip(d_pts, outs):
+            check(_lib.lib().dpf_amd_dcf_evaluate(
+                items, dptr(c_seeds), dptr(c_cb), dptr(c_party), dptr(d_x), H, tree_c,
+                dptr(c_cw), dptr(c_ccl), dptr(c_ccr), ctypes.byref(desc), dptr(c_corr), dptr(o),
+                stream_ptr()))
+
+    kt = {"fused": [], "composed": []}
+    for _ in range(3):
+        kt["fused"].append(ev_time(fused, reps))
+        kt["composed"].append(ev_time(composed, reps))
+    # the kernels agree: y = z - s_p + s_q' for party 0
+    s = [kernels.tensor_u128(o) for o in outs]
+    yf = kernels.tensor_u128(out_f)
+    zs = [pairs[i][0].output_mask_share for i in sel]
+    same = all(yf[i] == (zs[i // m][i % m] - s[0][i] + s[1][i]) % N
+               for i in range(0, items, max(1, items // 4096)))
+    same = same and yf == f0
+    # algorithmic AES of an item: both chains' tree levels + one value hash
+    # per 0 bit of each point (what the dcf config counts per evaluation)
+    sample = pts[0][:4096] + pts[1][:4096]
+    zeros = sum(H - bin(v).count("1") for v in sample) / len(sample)
+    aes = items * 2 * (L + zeros)
+    med = lambda v: float(np.median(v))  # noqa: E731
+    return {"keys": nkeys, "intervals": m, "log_group_size": n_log,
+            "api_fused_ms": med(api[0]) * 1e3, "api_composed_ms": med(api[1]) * 1e3,
+            "api_fused_ms_trials": [t * 1e3 for t in api[0]],
+            "api_composed_ms_trials": [t * 1e3 for t in api[1]],
+            "kernel_fused_ms": med(kt["fused"]) * 1e3,
+            "kernel_composed_ms": med(kt["composed"]) * 1e3,
+            "kernel_fused_ms_trials": [t * 1e3 for t in kt["fused"]],
+            "kernel_composed_ms_trials": [t * 1e3 for t in kt["composed"]],
+            "aes_per_item": aes / items,
+            "fused_lds_frac": lds_frac(aes / med(kt["fused"])),
+            "composed_lds_frac": lds_frac(aes / med(kt["composed"])),
+            "kernels_equal": bool(same), "correct": bool(ok)}
+
+
+def mic(dev, reps):
+    """MIC gate BatchEval at log_group_size 64: the reference benchmark's
+    1000 keys x 10 intervals (multiple_interval_containment_benchmark.cc) and
+    2^16 keys x 10 intervals."""
+    return {"config": "mic", "workload": "MIC gate BatchEval log_group_size=64, 10 intervals",
+            "shapes": [_mic_shape(dev, reps, 1000, 10, 64, 1000),
+                       _mic_shape(dev, reps, 1 << 16, 10, 64, 1024)]}
+
+
 def cuckoo(dev, reps):
     from distributed_point_functions_amd import cuckoo_pir as C
     from distributed_point_functions_amd import dpf as D
@@ -565,7 +708,7 @@ def cpp4(dev, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="c1,c2,c3,c4q,dcf,cuckoo,cpp")
+    ap.add_argument("--only", default="c1,c2,c3,c4q,dcf,mic,cuckoo,cpp")
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--c4q-queries", default=None, help="comma list, e.g. 64 (profiling)")
     ap.add_argument("--no-ab", action="store_true", help="c4q: skip the kernel A/B")
